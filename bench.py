@@ -10,7 +10,10 @@ A step = one pass of the hot path (gnnsaft_forward: CSR build, embeddings, L PNA
 add-pool, readout MLP, MAPE) over one HBM-resident batch, plus -- for N > 1 -- the RCCL
 all-reduce of [sum(ape), count] that the reference performs for its `sync_dist=True` loss
 metric.  Weak scaling: every rank owns its own G graphs; there is no data-path collective.
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line; `ms_per_step` is the wall time of one of the `--steps` timed steps.
+`--dump-outputs DIR`: rank 0 writes what the timed path handed its caller in the last timed step as DIR/<name>.npy
+(`predictions` [G,P] and `loss_parts` [mape, sum(ape), count]; `--config 5`: `loss` and the updated `parameters`).
+The inputs and initial weights are seeded, so two builds run with the same arguments can be compared file by file.
 
 `--config 2` (default) is BASELINE.json configs[1], the configuration the metric is quoted on; the N = 1 line
 also carries a `c3` block (configs[2], beyond the 256 MiB Infinity Cache: the HBM-honest roofline figures), and every
@@ -307,7 +310,11 @@ def main() -> None:
     ap.add_argument("--no-c3", action="store_true", help="skip the secondary C3 roofline block of the N = 1 line")
     ap.add_argument("--no-c4", action="store_true", help="skip the C4 block (8192 graphs per rank, H=256 L=5) of an N > 1 line")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from gnn_epc_saft_amd import parallel
 
@@ -342,8 +349,13 @@ def main() -> None:
         pending.append(parallel.global_mape_async(parts))
         return pending[-1]
 
+    target = ddev.para.view(-1, cfg["num_para"])
+
     def step():
-        return exchange(model.training_step_parts(ddev))       # [mape, sum(ape), count] on device
+        # what model.training_step_parts(ddev) computes, with the predictions kept for --dump-outputs:
+        # (pred [G,P], [mape, sum(ape), count], the loss after the exchange), all on device
+        pred, parts = model.model.run(ddev, target=target)
+        return pred, parts, exchange(parts)
 
     def drain():
         if not pending:
@@ -366,7 +378,7 @@ def main() -> None:
     # The captured graph holds the forward + loss kernels only; for N > 1 the (tiny) loss exchange is issued
     # right behind every replay, outside the graph (RCCL inside a captured graph is not exercised here).
     use_graph = bool(args.graph)
-    graph, parts_static, graph_note = None, None, None
+    graph, pred_static, parts_static, graph_note = None, None, None, None
     with torch.no_grad():
         with torch.cuda.stream(stream):
             for _ in range(max(args.warmup, 1) if use_graph else args.warmup):
@@ -381,7 +393,7 @@ def main() -> None:
                 cap_stream.wait_stream(stream)
                 g_obj = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g_obj, stream=cap_stream, capture_error_mode="thread_local"):
-                    parts_static = model.training_step_parts(ddev)
+                    pred_static, parts_static = model.model.run(ddev, target=target)
                 stream.wait_stream(cap_stream)
                 with torch.cuda.stream(stream):
                     g_obj.replay()
@@ -397,7 +409,7 @@ def main() -> None:
 
         def replay_step():
             graph.replay()
-            return exchange(parts_static)
+            return pred_static, parts_static, exchange(parts_static)
 
         run = replay_step if graph is not None else step
 
@@ -405,10 +417,12 @@ def main() -> None:
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            loss = run()
+            out = run()
         last = barrier()
         elapsed = time.perf_counter() - t0
-        final_loss = last if last is not None else loss
+        final_loss = last if last is not None else out[2]
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"predictions": out[0], "loss_parts": out[1]})
 
         # ---- the same K steps launched eagerly (one C call per step), for the record
         barrier()
@@ -584,6 +598,25 @@ def main() -> None:
     if flags["any"]:
         raise SystemExit(f"bench.py: GNNSAFT_FLAG_* bits raised during the run: {flags} "
                          "(16 = BARRIER_TIMEOUT of the fused readout: results invalid)")
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory: str, tensors) -> None:
+    """--dump-outputs: each tensor as ``directory/<name>.npy`` (float32 / float64 as computed), so that two builds can
+    be compared output for output on the same seeded inputs."""
+    import numpy as np
+    arrays = {name: t.detach().cpu().numpy() for name, t in tensors.items()}
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"--dump-outputs: {name} is {a.dtype}, not float32 / float64")
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), a)
 
 
 def reduce_flags(words, dev, world):
@@ -828,6 +861,9 @@ def bench_training_loop(args, dev, rank: int, world: int) -> None:
         loss = train_step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(1),
+                                         "parameters": torch.cat([p.detach().reshape(-1) for p in lit.parameters()])})
     t = torch.tensor([elapsed, float(seen[0])], dtype=torch.float64, device=dev)
     if world > 1:
         tm = t[:1].clone()

@@ -157,10 +157,10 @@ def training_loop(lit: PNApcsaftL, batches: Iterable, max_steps: Optional[int] =
 
 class GraphedTrainingStep:
     """One training step on a FIXED batch -- ``training_step`` (gnnsaft_forward with tape + MAPE), ``backward``
-    (gnnsaft_mape_backward + gnnsaft_backward on two streams), fused AdamW step -- captured once in a hipGraph and
-    replayed: ~140 launches and ~1.5 ms of host work per step become one graph launch.  Every replay trains on the
-    SAME batch object (same tensors; their contents may be overwritten in place between replays), so this serves
-    fixed-shape training and measurement, not a loader of ragged batches.
+    (gnnsaft_mape_backward + gnnsaft_backward, one stream inside the capture), fused AdamW step -- captured once in a
+    hipGraph and replayed: ~140 launches and ~1.5 ms of host work per step become one graph launch.  Every replay
+    trains on the SAME batch object (same tensors; their contents may be overwritten in place between replays), so
+    this serves fixed-shape training and measurement, not a loader of ragged batches.
 
     The optimizer must be a ``FusedAdamW`` (it is switched to ``capturable``: learning rate and bias corrections are
     read from device memory that ``prepare_replay()`` rewrites with a one-thread launch in front of every replay --
@@ -173,7 +173,7 @@ class GraphedTrainingStep:
                  trial_steps: int = 6):
         """``choose="auto"``: after the capture, ``trial_steps`` replays and ``trial_steps`` eager steps are timed (all of
         them real training steps) and ``__call__`` uses the faster form from then on (``self.mode``, ``self.trial_ms``):
-        the eager step overlaps its two backward streams, a replayed graph realises only part of that overlap, so on
+        the eager step overlaps its two backward streams, a replayed graph runs the backward on one stream, so on
         large batches the eager step can be the faster one."""
         from .optim import FusedAdamW
         if not isinstance(optimizer, FusedAdamW):
@@ -191,10 +191,18 @@ class GraphedTrainingStep:
         torch.cuda.synchronize(dev)
         self.graph = torch.cuda.CUDAGraph()
         optimizer.zero_grad(set_to_none=True)      # the captured backward then owns one static flat gradient buffer
-        with torch.cuda.graph(self.graph):
-            self.loss = lit.training_step(batch)
-            self.loss.backward()
-            optimizer.step()                       # records copy + kernel; counts nothing (prepare_replay does)
+        # The backward is captured on ONE stream: a graph whose backward forked onto the side stream inside the capture
+        # (issued from autograd's device thread, not the capturing thread) crashed the host in hipGraphLaunch on
+        # replay on MI355X.  A single-stream capture replays as fast and computes the same bits;
+        # eager steps keep the two-stream backward.
+        side, lit.model.backward_side_stream = lit.model.backward_side_stream, False
+        try:
+            with torch.cuda.graph(self.graph):
+                self.loss = lit.training_step(batch)
+                self.loss.backward()
+                optimizer.step()                   # records copy + kernel; counts nothing (prepare_replay does)
+        finally:
+            lit.model.backward_side_stream = side
         self.mode, self.trial_ms = "graph", None
         if choose == "auto":
             import time

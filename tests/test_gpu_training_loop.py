@@ -256,8 +256,8 @@ def test_graphed_training_step_equals_eager_steps(two_streams):
     import gnn_epc_saft_amd as G
     lit_a, batches, _ = _setup()
     lit_b, _, _ = _setup()
-    # the backward's side stream forks from and joins the capturing stream inside the capture (both modules alike:
-    # the two schedules give the same bits, test_backward_schedules_agree)
+    # the eager steps (lit_a's, lit_b's warm-up) run the backward on one or two streams; the capture itself is always
+    # single-stream (GraphedTrainingStep) -- the schedules give the same bits, test_backward_schedules_agree
     lit_a.model.backward_side_stream = lit_b.model.backward_side_stream = two_streams
     batch = batches[0]
     steps, warm = 7, 2
@@ -278,6 +278,7 @@ def test_graphed_training_step_equals_eager_steps(two_streams):
     opt_b, sched_b = conf["optimizer"], conf["lr_scheduler"]["scheduler"]
     lit_b.train()
     graphed = G.GraphedTrainingStep(lit_b, opt_b, batch, scheduler=sched_b, warmup=warm)
+    assert lit_b.model.backward_side_stream == two_streams      # the capture's single stream is not left behind
     losses_b = [float(graphed()) for _ in range(steps - warm)]
     torch.cuda.synchronize()
     assert losses_b == losses_a[warm:]
